@@ -13,20 +13,29 @@ gathered to rank 0 over RCCL each step -> "scaling": "strong". The draw goes thr
   python bench.py --gpus N                      one process drives N devices: rtx_create_multi(..., RTX_GATHER_RCCL), one rtx_draw per step
   python -m torch.distributed.run ... bench.py  one process per GPU: every rank holds an rtx_create_rank context (RCCL communicator from a
                                                 unique id that torch.distributed only hands round), one rtx_draw per step on every rank
-(--launcher torch makes the first form re-exec itself as the second; --transport torch keeps the round-1/2 Python path, bands.py +
+(--launcher torch makes the first form start the second as a child process; --transport torch keeps the round-1/2 Python path, bands.py +
 dist.gather, for comparison.) The target is the same at every N (default: the RGBA32F parity buffer the metric is defined on; --target
 rgba8 traces and gathers what the reference's framebuffer holds, GLWrapper.cpp:127,209-222, a quarter of the bytes), so a 1/2/4/8 series
 is one workload. A box with fewer than N GPUs answers --gpus N with one line and exit code 2.
+
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does what the headline figure needs and nothing else: set-up, the untimed ray
+count of the frame, the clock ramp, W warm-up steps, K timed steps, the line. --full adds the untimed measurements and checks below
+(cpu_baseline, parity, animated, smaa; for N > 1 the other colour target / band layout and the parity against one device).
+--dump-outputs DIR writes the frame of the last timed step as float32 .npy files (the whole frame up to 48 MB, above that a fixed seeded
+sample of its pixels with their indices), so that two builds can be compared output for output: the inputs are seeded, the same
+arguments give the same scene and textures in every run.
 
 Extra objects on the JSON line:
   roofline     HBM-write roofline of the trace kernel: W*H*16 B of RGBA32F per launch / mean kernel
                time from HIP events on the launch stream, against 8 TB/s; .valu = the ceiling that actually binds
                (VALU instructions per launch from profiles/valu.json / live duration vs the chip's issue rate).
-  cpu_baseline the oracle (scalar C restatement of the shader) on the CPUs this container may use (affinity mask capped by the cgroup
+  cpu_baseline (--full) the oracle (scalar C restatement of the shader) on the CPUs this container may use (affinity mask capped by the cgroup
                quota: 16 of the 256 hardware threads a GPU box shows), whole frames of the same workload for >= 10 s, rank 0, N = 1 only;
                with the one-thread rate and the parallel efficiency beside it.
   kernel_ms_stats  min / median / max of the timed draws' own HIP-event durations.
-  smaa         the SMAA post-process on the traced frame: time of one resolve and its HBM roofline (untimed addition).
+  smaa         (--full) the SMAA post-process on the traced frame: time of one resolve and its HBM roofline (untimed addition).
+  animated     (--full) kernel time of the default scene at other animation times.
+  parity       (--full) the full frame against the oracle (N = 1) or against one device tracing the whole frame (N > 1).
 """
 from __future__ import annotations
 
@@ -59,6 +68,25 @@ def emit(out):
 
 
 _JSON_OUT = None
+
+DUMP_WHOLE_BYTES = 48 << 20      # --dump-outputs: a frame up to this size goes whole, a larger one as a sample of pixels
+DUMP_SAMPLE_PIXELS = 1 << 20     # 16 MB of RGBA float32 + 8 MB of pixel indices
+DUMP_SEED = 20240611
+
+
+def dump_outputs(dirname, name, frame):
+    """--dump-outputs: the (H, W, 4) frame a caller of the timed path receives (row 0 = bottom row), as float32 (an RGBA8 target as 0..255).
+    Whole as <name>.npy while it fits DUMP_WHOLE_BYTES; otherwise <name>_sample.npy = (n, 4) pixels at the flat indices y * W + x held by
+    <name>_sample_pixel.npy (float64), drawn without replacement by a fixed seed -- the same pixels for the same frame size in every run."""
+    os.makedirs(dirname, exist_ok=True)
+    a = np.ascontiguousarray(frame, dtype=np.float32)
+    if a.nbytes <= DUMP_WHOLE_BYTES:
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+        return
+    px = a.reshape(-1, a.shape[-1])
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(px.shape[0], size=min(DUMP_SAMPLE_PIXELS, px.shape[0]), replace=False))
+    np.save(os.path.join(dirname, f"{name}_sample.npy"), px[idx])
+    np.save(os.path.join(dirname, f"{name}_sample_pixel.npy"), idx.astype(np.float64))
 
 
 def keep_stdout_for_the_json_line():
@@ -184,17 +212,20 @@ def bench_c_boundary(args, mode, n_ranks, rank, local_rank):
     for _ in range(args.warmup):
         gl.draw()
     elapsed, trace_ms_max, gather_ms = timed(args.steps)
+    fmt = wrapper.RTX_RGBA32F if target == "rgba32f" else wrapper.RTX_RGBA8
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, "frame", gl.read_pixels(fmt))   # the frame of the last timed step, assembled on rank 0
     ranks_trace_ms = rank_ms()
     layout_name = {"interleaved": "interleaved 8-row bands", "contiguous": "contiguous equal ranges", "balanced": "contiguous ranges weighted by kernel time"}[args.bands]
     gather_rgb = bool(gl.get_option(wrapper.RTX_OPT_GATHER_RGB))
     split_used = gl.band_split()
     st_end = gl.stats()
 
-    # Untimed additions to the SAME line (one run on an 8-GPU node is all there may be): the other colour target and the other band layout,
-    # each timed exactly like the value above, with K steps.
+    # Untimed additions to the SAME line with --full (one run on an 8-GPU node is all there may be): the other colour target and the other band
+    # layout, each timed exactly like the value above, with K steps.
     extras = {}
     try:
-        if n_ranks > 1 or args.transport == "loopback":
+        if args.full and (n_ranks > 1 or args.transport == "loopback"):
             other_target = "rgba8" if target == "rgba32f" else "rgba32f"
             gl.set_option(wrapper.RTX_OPT_GATHER_TARGETS, 2 if other_target == "rgba8" else 1)
             for _ in range(3):
@@ -234,17 +265,20 @@ def bench_c_boundary(args, mode, n_ranks, rank, local_rank):
     if rank != 0:
         gl.stop()
         return
-    # the assembled frame against ONE device tracing all of it (untimed): bit-identical or the split is wrong
-    fmt = wrapper.RTX_RGBA32F if target == "rgba32f" else wrapper.RTX_RGBA8
-    got = gl.read_pixels(fmt)
-    gl.stop()
-    one = wrapper.make_renderer(sc, W, H, ts["textures"], ts["cubemap"], device=local_rank, texture_lod=args.lod)
-    for o, v in ((wrapper.RTX_OPT_CULL, args.cull), (wrapper.RTX_OPT_SCENE_LDS, args.lds), (wrapper.RTX_OPT_XCD_REMAP, args.xcd), (wrapper.RTX_OPT_RAY_PENCILS, args.pencils)):
-        one.set_option(o, v)
-    one.draw()
-    want = one.read_pixels(fmt)
-    one.stop()
-    same = bool(np.array_equal(got.view(np.uint32 if target == "rgba32f" else np.uint8), want.view(np.uint32 if target == "rgba32f" else np.uint8)))
+    same = None
+    if args.full:
+        # the assembled frame against ONE device tracing all of it (untimed): bit-identical or the split is wrong
+        got = gl.read_pixels(fmt)
+        gl.stop()
+        one = wrapper.make_renderer(sc, W, H, ts["textures"], ts["cubemap"], device=local_rank, texture_lod=args.lod)
+        for o, v in ((wrapper.RTX_OPT_CULL, args.cull), (wrapper.RTX_OPT_SCENE_LDS, args.lds), (wrapper.RTX_OPT_XCD_REMAP, args.xcd), (wrapper.RTX_OPT_RAY_PENCILS, args.pencils)):
+            one.set_option(o, v)
+        one.draw()
+        want = one.read_pixels(fmt)
+        one.stop()
+        same = bool(np.array_equal(got.view(np.uint32 if target == "rgba32f" else np.uint8), want.view(np.uint32 if target == "rgba32f" else np.uint8)))
+    else:
+        gl.stop()
     ms_per_step = elapsed / args.steps * 1e3
     rows0 = split_used[0]
     achieved = rows0 * W * px_bytes / (trace_ms_max * 1e-3) / 1e9
@@ -288,10 +322,11 @@ def bench_c_boundary(args, mode, n_ranks, rank, local_rank):
                      "note": f"rank 0's launch: its {rows0} rows of the {target.upper()} frame ({px_bytes} B/pixel) / the slowest rank's mean kernel time; "
                              "the path is bound by VALU issue (DESIGN.md); gather_ms = transfer + band placement of the last frame on rank 0's "
                              "transfer stream (overlaps the next frame's trace)"},
-        "parity": {"vs_one_device_tracing_the_whole_frame": "bit-identical" if same else "DIFFERENT", "checked": target.upper()},
     }
+    if same is not None:
+        out["parity"] = {"vs_one_device_tracing_the_whole_frame": "bit-identical" if same else "DIFFERENT", "checked": target.upper()}
     emit(out)
-    if not same:
+    if same is False:
         raise SystemExit("bench.py: the gathered frame differs from the single-device frame")
 
 
@@ -324,7 +359,7 @@ def main():
                     help="N > 1: also time the other band layout (config.also_measured.bands_*). Off by default: measured alone on one GPU the contiguous "
                          "ranges lose to interleaved bands at every N (profiles/r04_time_bands_*.txt), and the line's run on real devices should not "
                          "depend on a second layout's code")
-    ap.add_argument("--no-smaa", action="store_true", help="skip the untimed SMAA post-process measurement (N = 1)")
+    ap.add_argument("--no-smaa", action="store_true", help="--full: skip the untimed SMAA post-process measurement (N = 1)")
     ap.add_argument("--launcher", choices=("auto", "torch"), default="auto",
                     help="N > 1 without torch.distributed.run around it: auto = one process drives the N devices through rtx_create_multi; "
                          "torch = re-exec this script under torch.distributed.run (one process per GPU, rtx_create_rank)")
@@ -333,6 +368,12 @@ def main():
                          "the root (single-process form only); torch = the Python path (bands.py, dist.gather; torch.distributed.run form only); "
                          "loopback = rccl with rank 0's own bands sent to itself as well -- a diagnostic that runs the N > 1 code, RCCL included, "
                          "on a box with one GPU (--gpus 1 --transport loopback)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the untimed measurements and checks beside the headline figure: cpu_baseline and full-frame parity against the "
+                         "oracle, animated, smaa (N = 1); the other colour target / band layout and the parity against one device (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step to DIR as float32 .npy (whole up to 48 MB, else a fixed seeded sample of pixels); "
+                         "bench_outputs/ inside the tree is git-ignored")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -348,13 +389,15 @@ def main():
         print(f"bench.py: --gpus {args.gpus} requested but this box has {n_dev} GPU{'s' if n_dev != 1 else ''}", file=sys.stderr, flush=True)
         raise SystemExit(2)
     if not under_torchrun and args.gpus > 1 and (args.launcher == "torch" or args.transport == "torch"):
-        # the one-process-per-GPU form, started from here (what the driver does itself for N > 1)
+        # the one-process-per-GPU form, started from here (what the driver does itself for N > 1) as a child process: this one has already
+        # initialised the HIP runtime (device count above)
         import socket
+        import subprocess
         with socket.socket() as so:
             so.bind(("127.0.0.1", 0))
             port = so.getsockname()[1]
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        raise SystemExit(subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
+                                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]).returncode)
     keep_stdout_for_the_json_line()
     # how the N ranks are driven: "single" = plain context (N = 1); "multi" = one process, rtx_create_multi; "ranks" = one process per GPU,
     # rtx_create_rank; "torch" = one process per GPU, rtx_draw_bands + dist.gather (the Python path)
@@ -423,9 +466,10 @@ def main():
         gl.draw_bands(band_rows, rank, world, buf.data_ptr(), tgt_format, stream)
         pending[k & 1] = gather.gather(buf, k & 1)  # async; overlaps the next step's trace (recv slot k&1 on the root)
 
-    def drain(pending):
+    def drain(pending, last=1):
+        """retire both slots, slot `last` (the one the latest step used) last; -> its frame"""
         out = None
-        for j in (0, 1):
+        for j in (1 - last, last):
             if pending[j] is not None:
                 out = gather.frame(pending[j])
                 pending[j] = None
@@ -449,12 +493,14 @@ def main():
     t0 = time.perf_counter()
     for k in range(args.steps):
         step(k, pending)
-    frame = drain(pending)
+    frame = drain(pending, (args.steps - 1) & 1)
     torch.cuda.synchronize(device)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize(device)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and frame is not None:
+        dump_outputs(args.dump_outputs, "frame", frame.cpu().numpy())
 
     n_ev = min(args.steps, 128)
     each_ms = sorted(gl.recent_draw_ms(n_ev))       # the spread of the timed draws: a 9 ms window is not the whole measurement
@@ -562,7 +608,7 @@ def main():
             if t:
                 out["roofline"]["traffic"] = t["hbm_bytes_per_launch"]
                 out["roofline"]["traffic_over_algorithmic"] = round(t["hbm_bytes_per_launch"] / float(W * H * px_bytes), 3)
-        if world == 1 and args.scene == "default":
+        if args.full and world == 1 and args.scene == "default":
             # The reference animates every frame (main.cpp:197-246: update_scene + an update_buffer of every block); the line above times the
             # t = 0 frame. Untimed addition: the kernel time of the same workload at other animation times, blocks re-uploaded like the
             # reference does (SceneUploader.update), 10 launches each.
@@ -581,7 +627,7 @@ def main():
             out["animated"] = {"kernel_ms_per_frame": anim, "mean_ms": round(sum(anim.values()) / len(anim), 4),
                                "note": "default scene at animation times t (update_scene of main.cpp:197-246 with time = deltaTime = t, every block "
                                        "re-uploaded); value / ms_per_step above are the t = 0 frame"}
-        if world == 1 and not args.no_smaa:
+        if args.full and world == 1 and not args.no_smaa:
             # the post-process that follows the tracer in the reference's draw(). Untimed addition to the line: ULTRA (main.cpp:32)
             # on the frame just traced, HIP events around the four kernels of one resolve. Algorithmic bytes: W*H*4 read + W*H*4 written.
             gl.enable_SMAA(wrapper.ULTRA)   # the library's own area / search tables (== the reference's arrays, include/rtx/smaa_tables.h)
@@ -604,7 +650,7 @@ def main():
                            "note": "all kernels of one resolve of the traced frame (RGBA8 in, RGBA8 screen out); area and search tables generated "
                                    "by the library, byte-identical to the reference's AreaTex.h / SearchTex.h (tests/test_smaa_tables.py); "
                                    "byte-exact against the oracle in tests/test_gpu_smaa.py"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle import oracle
             o = oracle.OracleScene(sc, W, H, ts["textures"], ts["cubemap"], texture_lod=args.lod)
             cores, cpu_quota = oracle.effective_cpus()

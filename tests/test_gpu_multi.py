@@ -301,7 +301,7 @@ def _run_bench(extra, torchrun=False, timeout=600):
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     head = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1", "--master-port", "29533"] if torchrun else [sys.executable]
-    cmd = head + [os.path.join(root, "bench.py"), "--width", "640", "--height", "360", "--steps", "4", "--warmup", "2", "--texture-scale", "16", "--no-cpu-baseline", "--no-smaa"] + extra
+    cmd = head + [os.path.join(root, "bench.py"), "--width", "640", "--height", "360", "--steps", "4", "--warmup", "2", "--texture-scale", "16", "--full", "--no-cpu-baseline", "--no-smaa"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if r.returncode == 0:   # stdout is the ONE line of JSON and nothing else (RCCL's version banner used to precede it)

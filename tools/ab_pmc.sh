@@ -3,7 +3,7 @@
 R=$(pwd); export TMPDIR=/tmp; cd /tmp
 for lib in $R/raytracing_opengl_amd/librtx_hip.so $R/raytracing_opengl_amd/variants/*.so; do
   tag=$(basename $lib .so); rm -rf /tmp/abpmc_$tag
-  RTX_HIP_LIB=$lib rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_THREAD_CYCLES_VALU --output-format csv -d /tmp/abpmc_$tag -- python $R/bench.py --no-cpu-baseline --steps 5 --warmup 2 ${AB_BENCH_ARGS:-} > /tmp/abpmc_$tag.log 2>&1
+  RTX_HIP_LIB=$lib rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_THREAD_CYCLES_VALU --output-format csv -d /tmp/abpmc_$tag -- python $R/bench.py --full --no-cpu-baseline --steps 5 --warmup 2 ${AB_BENCH_ARGS:-} > /tmp/abpmc_$tag.log 2>&1
   python3 - $tag <<'PY'
 import csv,glob,collections,sys
 acc=collections.defaultdict(list)

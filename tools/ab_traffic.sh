@@ -4,7 +4,7 @@ for lib in $R/raytracing_opengl_amd/librtx_hip.so $R/raytracing_opengl_amd/varia
   tag=$(basename $lib .so)
   for ctr in WRITE_SIZE FETCH_SIZE; do
   rm -rf /tmp/abt_$tag
-  RTX_HIP_LIB=$lib rocprofv3 --pmc $ctr --output-format csv -d /tmp/abt_$tag -- python $R/bench.py --no-cpu-baseline --steps 5 --warmup 2 > /tmp/abt_$tag.log 2>&1
+  RTX_HIP_LIB=$lib rocprofv3 --pmc $ctr --output-format csv -d /tmp/abt_$tag -- python $R/bench.py --full --no-cpu-baseline --steps 5 --warmup 2 > /tmp/abt_$tag.log 2>&1
   python3 - $tag <<'PY'
 import csv,glob,collections,sys
 acc=collections.defaultdict(list)

@@ -41,13 +41,13 @@ gpu)
 final)  # the round's final measurements: kernel-trace + PMC passes of the three bench scenes (-> profiles/valu*.json, traffic*.json through
         # tools/prof_to_json.py), the bench line of every configuration, the driver's line under rocprofv3 (kernel-trace), the SMAA split
   bash tools/profile_configs.sh r06 > $O/profile_configs.log 2>&1; tail -5 $O/profile_configs.log
-  ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/bench_trace -- python $GRAFT_REPO_ROOT/bench.py > $GRAFT_REPO_ROOT/$O/bench_n1_under_rocprof.json 2> $GRAFT_REPO_ROOT/$O/bench_n1_under_rocprof.err )
-  python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
-  python bench.py --scene quadric --no-cpu-baseline > $O/bench_n1_quadric.json 2>/dev/null
-  python bench.py --scene torus --depth 6 --no-cpu-baseline > $O/bench_n1_torus.json 2>/dev/null
-  python bench.py --width 1920 --height 1080 --no-cpu-baseline > $O/bench_config1_1080p.json 2>/dev/null
-  python bench.py --width 7680 --height 4320 --no-cpu-baseline > $O/bench_config4_8k_1gpu.json 2>/dev/null
-  python bench.py --gpus 1 --transport loopback --no-cpu-baseline --also-bands > $O/bench_loopback_multi.json 2>/dev/null
+  REPO=$(pwd); ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$O/bench_trace -- python $REPO/bench.py --full > $REPO/$O/bench_n1_under_rocprof.json 2> $REPO/$O/bench_n1_under_rocprof.err )
+  python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
+  python bench.py --full --scene quadric --no-cpu-baseline > $O/bench_n1_quadric.json 2>/dev/null
+  python bench.py --full --scene torus --depth 6 --no-cpu-baseline > $O/bench_n1_torus.json 2>/dev/null
+  python bench.py --full --width 1920 --height 1080 --no-cpu-baseline > $O/bench_config1_1080p.json 2>/dev/null
+  python bench.py --full --width 7680 --height 4320 --no-cpu-baseline > $O/bench_config4_8k_1gpu.json 2>/dev/null
+  python bench.py --full --gpus 1 --transport loopback --no-cpu-baseline --also-bands > $O/bench_loopback_multi.json 2>/dev/null
   for f in $O/bench_*.json; do python - $f <<'PY'
 import json,sys
 try:
